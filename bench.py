@@ -6,6 +6,8 @@
                                                               # torch.distributed.run with 8 ranks (RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR   # also writes the last timed step's results as
+                                                                        # DIR/*.npy (float32; see dump_outputs)
 
 One "step" = one full optimisation step of the hot path on one batch of synthetic input per GPU: frozen
 ProteInfer encoder forward (train-mode BN) -> W_p / W_l -> pair-grid MLP head with train-mode BatchNorm over
@@ -658,6 +660,44 @@ def emit(full):
     print(headline(full), flush=True)
 
 
+DUMP_PARAM_SAMPLE = 1 << 16  # elements kept of a larger parameter (fixed, seeded sample); smaller ones are kept whole
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, loss, model, opt, counts):
+    """--dump-outputs DIR: what a caller of the timed train step holds after the LAST timed step, as float32 .npy files:
+      loss.npy                 [1]       the loss train_step returned
+      params.npy               [n]       the updated trainable parameters (optimiser order)
+      adam_exp_avg.npy         [n]       Adam's first moments at the same elements
+      adam_exp_avg_sq.npy      [n]       Adam's second moments at the same elements
+      bn_running_stats.npy     [m]       running_mean then running_var of every BatchNorm layer (model.modules() order)
+      label_counts.npy         [3, N_L]  per-label TP / FN / FP accumulated by the loss pass over warmup + timed steps
+    A parameter of more than DUMP_PARAM_SAMPLE elements contributes a sorted sample of that many, drawn without replacement
+    from a generator seeded with DUMP_SEED (the same elements on every run), so the files stay well under 64 MB."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    base = opt.flat_w.data_ptr()
+    idx = []
+    for p in opt.params:  # each parameter is a view of opt.flat_w; its moments sit at the same offsets of flat_m / flat_v
+        off, n = (p.data_ptr() - base) // opt.flat_w.element_size(), p.numel()
+        pick = np.arange(n) if n <= DUMP_PARAM_SAMPLE else np.sort(rng.choice(n, DUMP_PARAM_SAMPLE, replace=False))
+        idx.append(off + pick)
+    idx = torch.from_numpy(np.concatenate(idx)).to(opt.flat_w.device)
+    bn = [t for m in model.modules() if isinstance(m, torch.nn.BatchNorm1d) for t in (m.running_mean, m.running_var)]
+    out = {"loss": np.array([loss], dtype=np.float32),
+           "params": opt.flat_w[idx],
+           "adam_exp_avg": opt.flat_m[idx],
+           "adam_exp_avg_sq": opt.flat_v[idx],
+           "bn_running_stats": torch.cat([t.detach().float().reshape(-1) for t in bn]),
+           "label_counts": counts}
+    for name, a in out.items():
+        a = a.detach().float().cpu().numpy() if isinstance(a, torch.Tensor) else a
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -677,7 +717,13 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the forward_only / zero_shot sub-benchmarks")
     ap.add_argument("--zero-shot-seqs", type=int, default=512,
                     help="sequences PER RANK in the zero_shot sub-benchmark (weak scaling, like the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one left the caller (loss, updated parameters and "
+                         "optimiser moments - a fixed sample of the large ones -, BatchNorm running statistics, label "
+                         "counts) to DIR/<name>.npy in float32 (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
@@ -788,6 +834,8 @@ def main():
 
     # ------------------------------------------------------------------ headline: train step
     elapsed, prof, loss_val, comm = timed_train(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:  # before the sub-benchmarks below train the same model further
+        dump_outputs(args.dump_outputs, loss_val, model, opt, counts)
     fast = None
     if args.math == "f32" and not args.no_fast_mode:  # same workload once more on the opt-in bf16x3 arithmetic
         # (sub-benchmarks run a bounded number of steps: the default driver invocation is 20 + 5 of the 6.6 s headline step, and

@@ -17,6 +17,8 @@ What is executed (all f32, CPU, torch.manual_seed fixed):
   * protnote/data/collators.py           collate_variable_sequence_length
   * protnote/data/datasets.py            ProteinDataset label-index bookkeeping on a toy FASTA (vocabularies,
                                          multihots, embedding-row filter/sort/sample) - integer, bit-exact
+  * inspect.signature of the reference objects tests/test_signatures.py compares against (JSON), and
+    configs/base_config.yaml re-dumped as plain data (tests/test_config_surface.py)
 
 Absent third-party modules that are NOT on the arithmetic path are stubbed in sys.modules.
 torchvision.ops.MLP (pinned torchvision==0.15.2 in the reference's setup.py:17) is absent from this
@@ -1196,6 +1198,43 @@ def golden_config_holes():
         print(os.path.basename(fn), os.path.getsize(fn) // 1024, "KiB")
 
 
+def golden_signatures():
+    """inspect.signature of every reference object tests/test_signatures.py holds a twin to: parameter names, kinds and
+    default reprs (the test's own NAMES and _sig, so the fixture and the comparison cannot drift apart)."""
+    import importlib
+    import json
+
+    sys.path.insert(0, os.path.dirname(OUT))
+    from test_signatures import NAMES, _sig
+
+    res = {}
+    for n in NAMES:
+        mod, _, attr = n.partition(":")
+        o = importlib.import_module(mod)
+        for a in attr.split("."):
+            o = getattr(o, a)
+        res[n] = _sig(o)
+    fn = os.path.join(OUT, "reference_signatures.json")
+    with open(fn, "w") as f:  # one object per line
+        f.write("{\n" + ",\n".join(f" {json.dumps(n)}: {json.dumps(res[n])}" for n in sorted(res)) + "\n}\n")
+    print(os.path.basename(fn), len(res), "signatures")
+
+
+def golden_base_config():
+    """The reference's configs/base_config.yaml as data: parsed and dumped again (values only, no comments), checked to
+    load back to the same mapping."""
+    import yaml
+
+    with open(os.path.join(REF, "configs", "base_config.yaml")) as f:
+        cfg = yaml.safe_load(f)
+    text = yaml.safe_dump(cfg, sort_keys=False)
+    assert yaml.safe_load(text) == cfg
+    fn = os.path.join(OUT, "base_config.yaml")
+    with open(fn, "w") as f:
+        f.write(text)
+    print(os.path.basename(fn), len(text), "B")
+
+
 if __name__ == "__main__":
     install_stubs()
     torch.set_num_threads(8)
@@ -1205,7 +1244,8 @@ if __name__ == "__main__":
             "collator": golden_collator, "bookkeeping": golden_bookkeeping, "tf_weights": golden_tf_weights,
             "samplers": golden_samplers, "attention": golden_attention_pooling, "grid_samplers": golden_grid_samplers,
             "config0": golden_config0_full_width, "optimizer_branches": golden_optimizer_branches,
-            "disk_formats": golden_disk_formats, "config_holes": golden_config_holes}
+            "disk_formats": golden_disk_formats, "config_holes": golden_config_holes, "signatures": golden_signatures,
+            "base_config": golden_base_config}
     for name, fn in jobs.items():
         if not only or name in only:
             fn()

@@ -159,3 +159,64 @@ def test_cpu_legs_child_orders_its_samples(monkeypatch, capsys):
     assert calls == [(16, 2), (32, 2), (32, 4)]
     lines = [json.loads(ln) for ln in capsys.readouterr().out.strip().splitlines()]
     assert lines[-1] == {"threads": 64, "skipped": "budget"}
+
+
+def _flat_optimiser_stand_in(params):
+    """What dump_outputs reads of FusedClipAdam (flat weight / moment blocks, parameters as views of the weight block), on the
+    CPU: every parameter at a 16-byte aligned offset, as the optimiser lays them out."""
+    import types
+
+    import torch
+
+    sizes = [(p.numel() + 3) // 4 * 4 for p in params]
+    g = torch.Generator().manual_seed(3)
+    n = sum(sizes)
+    opt = types.SimpleNamespace(flat_w=torch.randn(n, generator=g), flat_m=torch.randn(n, generator=g),
+                                flat_v=torch.rand(n, generator=g), params=[])
+    off = 0
+    for p, sz in zip(params, sizes):
+        opt.params.append(opt.flat_w[off:off + p.numel()].view_as(p))
+        off += sz
+    return opt
+
+
+def test_dump_outputs_writes_float32_arrays_with_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files of the caller's results; a large parameter contributes the same seeded sample of
+    DUMP_PARAM_SAMPLE elements on every run, a small one all of its elements, each read at its own offset of the flat blocks."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_PARAM_SAMPLE", 64)
+    model = torch.nn.Sequential(torch.nn.Linear(20, 10), torch.nn.BatchNorm1d(10), torch.nn.Linear(10, 3))
+    params = list(model.parameters())  # 200, 10, 10, 10, 30, 3 elements: only the first is sampled
+    opt = _flat_optimiser_stand_in(params)
+    counts = torch.arange(3 * 7, dtype=torch.float32).reshape(3, 7)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), 0.25, model, opt, counts)
+    names = {"loss", "params", "adam_exp_avg", "adam_exp_avg_sq", "bn_running_stats", "label_counts"}
+    assert {f.name for f in (tmp_path / "a").iterdir()} == {n + ".npy" for n in names}
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    for n in names:
+        assert got[n].dtype == np.float32, n
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / (n + ".npy"))), n
+    assert got["loss"].tolist() == [0.25] and np.array_equal(got["label_counts"], counts.numpy())
+    assert got["params"].shape == (64 + 10 + 10 + 10 + 30 + 3,)
+    first = opt.params[0].detach().reshape(-1).numpy()
+    assert np.isin(got["params"][:64], first).all() and len(np.unique(got["params"][:64])) == 64
+    assert np.array_equal(got["params"][64:], np.concatenate([p.detach().reshape(-1).numpy() for p in opt.params[1:]]))
+    off = (opt.params[-1].data_ptr() - opt.flat_w.data_ptr()) // 4
+    assert np.array_equal(got["adam_exp_avg"][-3:], opt.flat_m[off:off + 3].numpy())
+    assert np.array_equal(got["adam_exp_avg_sq"][-3:], opt.flat_v[off:off + 3].numpy())
+    bn = model[1]
+    assert np.array_equal(got["bn_running_stats"], np.concatenate([bn.running_mean.numpy(), bn.running_var.numpy()]))
+
+
+def test_steps_must_be_positive(monkeypatch):
+    import bench
+
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2

@@ -110,18 +110,14 @@ def test_build_training_rejects_unknown_optimizer():
         CF.build_training(cfg, model=None)
 
 
-REAL_CONFIG = "/root/reference/configs/base_config.yaml"
-
-
-@pytest.mark.skipif(not __import__("os").path.exists(REAL_CONFIG),
-                    reason="the reference checkout only exists in the build container")
-def test_real_base_config_builds_and_embedded_copy_agrees():
-    """The reference's own configs/base_config.yaml (read in place - never copied into the repo): every key the
-    embedded test config above uses exists there with the same value, `--override` works on it, and
-    build_models / build_training accept it unmodified."""
+def test_real_base_config_builds_and_embedded_copy_agrees(golden_dir):
+    """The reference's own configs/base_config.yaml (its values, stored as tests/golden/base_config.yaml by
+    tests/golden/make_golden.py --base_config): every key the embedded test config above uses exists there with the same
+    value, `--override` works on it, and build_models / build_training accept it unmodified."""
     import copy
+    import os
 
-    real, root = CF.load_config(REAL_CONFIG)  # absolute path: taken as is, like the reference's pathlib join
+    real, root = CF.load_config(os.path.join(golden_dir, "base_config.yaml"))  # absolute path: taken as is, like the reference's pathlib join
     assert str(real["paths"]["data_paths"]["TRAIN_DATA_PATH"]).startswith(str(root / "data"))
     for section in ("params", "embed_sequences_params"):
         for k, v in CFG[section].items():

@@ -16,9 +16,41 @@ def _free_port():
     return p
 
 
+def _cpu_rank():
+    """The ranks here run the host-side plumbing on CPU tensors.  On a GPU box init_from_env would bind rank r to device r
+    (which a one-GPU box does not have) and every rank would open the device: keep them off it."""
+    torch.cuda.is_available = lambda: False
+
+
+def _spawn(target, world):
+    """Run target(rank, world, port, queue) in `world` fresh processes and return what each rank put on the queue,
+    unpickled.  Ranks still alive when this returns (a failed peer leaves the others waiting in the rendezvous) are
+    killed."""
+    import pickle
+
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=target, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    try:
+        res = [pickle.loads(q.get(timeout=120)) for _ in range(world)]
+        for p in procs:
+            p.join(timeout=60)
+            assert p.exitcode == 0
+        return res
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.kill()
+                p.join(timeout=10)
+
+
 def _worker(rank, world, port, q):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
+    _cpu_rank()
     from protnote_amd.utils import distributed as D
 
     r, _, w = D.init_from_env(backend="gloo")
@@ -67,19 +99,7 @@ def _worker(rank, world, port, q):
 
 
 def test_two_rank_gloo():
-    world = 2
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    import pickle
-
-    res = sorted((pickle.loads(q.get(timeout=120)) for _ in range(world)), key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    res = sorted(_spawn(_worker, 2), key=lambda t: t[0])
     want_g = torch.arange(10, dtype=torch.float32) * 1.5  # mean of x*1 and x*2
     seen = []
     for rank, g, rm, rv, counts, shard, _ in res:
@@ -129,6 +149,7 @@ def test_bench_self_launch_command(monkeypatch):
 def _exchange_worker(rank, world, port, q):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
+    _cpu_rank()
     from protnote_amd.utils import distributed as D
     from protnote_amd.utils.evaluation import DeviceAveragePrecision
 
@@ -147,19 +168,7 @@ def _exchange_worker(rank, world, port, q):
 def test_two_rank_variable_exchange():
     """The all-to-all of the rank-sharded exact AP (label blocks to their owner, key ranges to theirs): uneven and empty
     chunks arrive at the right rank in sender order."""
-    import pickle
-
-    world = 2
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_exchange_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = sorted((pickle.loads(q.get(timeout=120)) for _ in range(world)), key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    res = sorted(_spawn(_exchange_worker, 2), key=lambda t: t[0])
     r0, r1 = res[0][1], res[1][1]
     assert r0[0].tolist() == [0] and r0[1].tolist() == []                      # from rank 0: 1 element; from rank 1: empty
     assert r1[0].tolist() == [10, 11] and r1[1].tolist() == [110, 111, 112]    # from rank 0: 2; from rank 1: 3
@@ -192,6 +201,7 @@ def test_zero_shot_dealing_balances_eight_ranks():
 def _sgd_worker(rank, world, port, q):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
+    _cpu_rank()
     from protnote_amd.utils import distributed as D
 
     D.init_from_env(backend="gloo")
@@ -223,19 +233,7 @@ def _sgd_worker(rank, world, port, q):
 def test_two_rank_sync_with_sgd_shaped_optimizer():
     """OPTIMIZER: SGD under data parallelism (reference ProtNoteTrainer.py:238-243 + DDP): the optimiser has no second
     moment and, with momentum 0, no velocity block either; sync_initial_state must broadcast only what exists."""
-    import pickle
-
-    world = 2
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_sgd_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = dict(pickle.loads(q.get(timeout=120)) for _ in range(world))
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    res = dict(_spawn(_sgd_worker, 2))
     for case in range(2):
         w0, m0, s0, b0 = res[0][case]
         w1, m1, s1, b1 = res[1][case]

@@ -23,6 +23,14 @@ def _free_port():
     return p
 
 
+def _kill_survivors(procs):
+    """A rank whose peer failed waits in the rendezvous or a barrier with the GPU open: never leave one running."""
+    for p in procs:
+        if p.is_alive():
+            p.kill()
+            p.join(timeout=10)
+
+
 def _data():
     g = torch.Generator().manual_seed(3)
     n, nl = 601, 37  # odd: the two ranks hold shards of different size
@@ -109,10 +117,13 @@ def _run_two_ranks(backend):
     procs = [ctx.Process(target=_worker, args=(r, world, port, q, backend)) for r in range(world)]
     for p in procs:
         p.start()
-    res = sorted((q.get(timeout=300) for _ in range(world)), key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    try:
+        res = sorted((q.get(timeout=300) for _ in range(world)), key=lambda t: t[0])
+        for p in procs:
+            p.join(timeout=120)
+            assert p.exitcode == 0
+    finally:
+        _kill_survivors(procs)
     p, y = _data()
     per = np.array([MO.average_precision_fast(p[:, j].numpy(), y[:, j].numpy()) for j in range(p.shape[1])])
     micro = MO.average_precision_fast(p.numpy().ravel(), y.numpy().ravel())
@@ -205,10 +216,13 @@ def test_two_ranks_sgd_through_build_training():
     procs = [ctx.Process(target=_sgd_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
-    res = dict(q.get(timeout=300) for _ in range(world))
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    try:
+        res = dict(q.get(timeout=300) for _ in range(world))
+        for p in procs:
+            p.join(timeout=120)
+            assert p.exitcode == 0
+    finally:
+        _kill_survivors(procs)
     for case in range(2):
         np.testing.assert_array_equal(res[0][case], res[1][case])
         assert np.isfinite(res[0][case]).all()
@@ -343,10 +357,13 @@ def _run_sync_bn(train_encoder, mode):
     procs = [ctx.Process(target=_sync_bn_worker, args=(r, world, port, q, train_encoder, mode)) for r in range(world)]
     for p in procs:
         p.start()
-    res = sorted((pickle.loads(q.get(timeout=300)) for _ in range(world)), key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    try:
+        res = sorted((pickle.loads(q.get(timeout=300)) for _ in range(world)), key=lambda t: t[0])
+        for p in procs:
+            p.join(timeout=120)
+            assert p.exitcode == 0
+    finally:
+        _kill_survivors(procs)
     return res
 
 

@@ -12,6 +12,16 @@ from oracle import protnote_oracle as O
 FUSIONS = ("concatenation", "concatenation_diff", "concatenation_prod", "similarity")
 
 
+@pytest.fixture(autouse=True)
+def _golden_thread_count():
+    """The goldens were recorded with 8 threads (tests/golden/make_golden.py), and the f32 results of the CPU kernels depend on
+    how many threads split the reductions: replay them with the same, whatever the host's core count."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(n)
+
+
 def _load(golden_dir, name):
     return np.load(os.path.join(golden_dir, name))
 
